@@ -22,7 +22,7 @@ test-gpu: build
 
 bench: build
 	$(PY) -m torch.distributed.run --nnodes=1 --nproc-per-node $(N) --master-addr 127.0.0.1 --master-port 29511 \
-		bench.py --gpus $(N)
+		bench.py --gpus $(N) --full
 
 mpi-bench: build
 	/opt/conda/bin/mpirun -np $(N) bin/flexar_bench --mem host --size 1024 --repeat 200

@@ -13,14 +13,24 @@ the MAX over ranks is reported.
 
 Numbers (rccl-tests convention): algbw = bytes / t and busbw = algbw * 2 (N - 1) / N. `value` IS the
 busbw of BASELINE.json's metric, the figure rccl-tests prints (one number for the job: every rank moves
-the same bytes), so `value == busbw_GBps` for every N and the 1/2/4/8 series is one quantity;
+the same bytes), so `value == busbw_GBps` for every N >= 2 and the 2/4/8 series is one quantity;
 `vs_baseline` compares it with the reference's busbw. At N = 1 the busbw factor 2(N-1)/N is 0 (no
-inter-GPU traffic), so `value` is 0 there by definition; the device-copy algbw of that run is reported
-separately as `algbw_GBps` and is not comparable with busbw. `aggregate_busbw_GBps` (busbw x N) is kept
-as an extra key for whole-job accounting.
+inter-GPU traffic), so `busbw_GBps` is 0 there by definition and says nothing about the run: a one-GPU run
+would have no figure to compare between two builds. There `value` is the algbw of the same timed steps
+(bytes / t, `value == algbw_GBps`: the device copy through the executor kernel), which is not comparable
+with the busbw of N >= 2; `value_definition` in the line says which of the two it is.
+`aggregate_busbw_GBps` (busbw x N) is kept as an extra key for whole-job accounting.
 
-At N >= 2 the same JSON line also measures every other BASELINE config, OUTSIDE the headline's timed
-region, each next to RCCL and timed max-over-ranks:
+A plain run does only what the headline needs: set-up (at N >= 2 the start-up tuner that picks the timed
+schedule), the correctness gate around the timed region, warm-up, the timed steps and the JSON line.
+`--dump-outputs DIR` also writes what the last timed step returned as DIR/allreduce_out.npy (float32; rank r > 0
+writes allreduce_out_rank<r>.npy): the whole result, or a fixed seeded sample of a larger one. The inputs are
+seeded, so two builds run with the same arguments can be compared output for output. Everything below is
+measured only with `--full`.
+
+With `--full`, at N = 1 the line also carries the fan-in reduction-kernel section (`reduce_kernel`) and the
+8-ranks-in-one-launch executor section (`group_executor`), and at N >= 2 it also measures every other BASELINE
+config, OUTSIDE the headline's timed region, each next to RCCL and timed max-over-ranks:
   config3  bf16 1 GiB: RHD with fp32 partials ("+f32"), RHD rounded per hop ("+rw") and the selector's own
            choice, each checked against an fp32 reference, next to RCCL bf16;
   config4  the 4 KiB -> 1 GiB (x4) sweep of the selector's choice, every size an exact-integer correctness
@@ -69,6 +79,7 @@ CALIB_SIZES = (64 << 10, 1 << 20, 8 << 20, 64 << 20)
 # only when the tuner alone has spent three quarters of the budget)
 DROP_AT = {"cost_model_fit": 0.5, "config4_tail": 0.65, "grid_sweep": 0.75}
 COMPANION_AT = 0.85  # config3 / config4 head / config5 / small messages
+DUMP_MAX_ELEMS = 4 << 20  # --dump-outputs: float32 elements over all ranks (16 MiB of .npy files)
 
 
 def write_line(fd: int, text: str):
@@ -274,7 +285,15 @@ def main():
     ap.add_argument("--reduce-kernel-mb", type=float, default=256.0, help="reduce_kernel: MiB per source")
     ap.add_argument("--no-group-executor", action="store_true",
                     help="N = 1: skip the 8-ranks-in-one-launch executor section (group_executor)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure everything beside the headline: the RCCL comparison, the cost model's own choice, "
+                         "BASELINE configs #3/#4/#5, the 8 KiB figure and the calibration mini-sweep (N > 1); the "
+                         "reduce_kernel and group_executor sections (N = 1)")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="write the result of the last timed step as DIR/allreduce_out.npy (float32; a fixed seeded "
+                         "sample if the result is larger than the cap)")
     args = ap.parse_args()
+    full = args.full  # False: a plain run, the headline alone (every companion section below asks `full` first)
 
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
         # no launcher: this process starts the N ranks itself (and never touches the GPU)
@@ -513,7 +532,7 @@ def main():
 
     # ---------------------------------------------------------------- cost model (no tune table)
     model = None
-    if world > 1 and not fallback:
+    if full and world > 1 and not fallback:
         ph("cost-model measurement")
         choice = comm.describe(count, dtype)
         spec0 = choice.split(" ")[0]
@@ -630,6 +649,13 @@ def main():
     # failure there - a protocol that passed the tuner's checks but not these, e.g. an intermittent visibility
     # problem on a node never seen before - must not lose the run: the next-fastest correct candidate takes
     # over (fresh communicator), then RCCL, and the JSON line names what was rejected and why.
+    dump_idx = dumped = None
+    if args.dump_outputs and count > DUMP_MAX_ELEMS // world:
+        # a result larger than the cap: a fixed sample of it (same seed, same arguments -> same elements)
+        import numpy as np
+
+        pick = np.sort(np.random.RandomState(20240607).randint(0, count, size=DUMP_MAX_ELEMS // world, dtype=np.int64))
+        dump_idx = torch.from_numpy(pick).to(dev)
     if not ranked:
         ranked = [(algo, None)]
     if world > 1 and not host_ref and algo != "rccl":
@@ -690,6 +716,9 @@ def main():
         torch.cuda.synchronize()
         elapsed, run_failed = max_vec([time.perf_counter() - t0, run_failed])
         t_step = elapsed / max(1, args.steps)
+        if args.dump_outputs and not run_failed:  # y as the last timed step left it (the check below overwrites it)
+            bits = {1: torch.uint8, 2: torch.int16, 4: torch.int32}[esize]  # gather on the bits: any dtype
+            dumped = (y if dump_idx is None else y.view(bits)[dump_idx].view(dtype)).float().cpu().numpy()
         # the timed calls must have produced correct results too (checked again right after, same protocol state)
         failed, err_after = check(algo) if not run_failed else (1.0, "a timed call failed")
         if max_over_ranks(failed) == 0.0:
@@ -701,9 +730,14 @@ def main():
         raise SystemExit(f"no algorithm passed the final checks: {rejected}")
     if rejected and tune_log is not None:
         tune_log["rejected_after_tuning"] = rejected
+    if args.dump_outputs:
+        import numpy as np
+
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        np.save(os.path.join(args.dump_outputs, "allreduce_out" + (f"_rank{rank}" if rank else "") + ".npy"), dumped)
 
     rccl_busbw = None
-    if world > 1 and not args.no_rccl and dtype != torch.float8_e4m3fn:
+    if full and world > 1 and not args.no_rccl and dtype != torch.float8_e4m3fn:
         z = x.clone()
         rt = timed_fn(lambda: dist.all_reduce(z), max(1, args.steps), max(1, args.warmup))
         rccl_busbw = round(busbw_gbps(nbytes, rt, world), 2) if rt else None
@@ -713,7 +747,7 @@ def main():
     ph("timed region done")
     sections = {}
     flex = not isinstance(comm, RcclOnly)
-    if world > 1 and flex and not args.no_configs:
+    if full and world > 1 and flex and not args.no_configs:
         ph("BASELINE configs #5 / #3 / #4")
         if budget.allow("config5", COMPANION_AT):
             sections["config5"] = run_config5(comm, world, dev, dist, timed_fn, max_vec, host_ref, args, rank)
@@ -731,7 +765,7 @@ def main():
     # latency-bound companion figure (outside the timed region): an 8 KiB fp32 allreduce, eager, the
     # selector's choice (LL), against RCCL's on the same buffer
     small = None
-    if world > 1 and not args.no_small and budget.allow("small_msg", COMPANION_AT):
+    if full and world > 1 and not args.no_small and budget.allow("small_msg", COMPANION_AT):
         xsm = torch.randn(2048, device=dev)
         ysm = torch.empty_like(xsm)
         tf = timed_fn(lambda: comm.all_reduce(xsm, out=ysm), 200, 20)
@@ -741,7 +775,7 @@ def main():
             small["rccl"] = round(tr * 1e6, 2) if tr else None
 
     # calibration mini-sweep of the tuner's candidates vs RCCL + the cost-model fit (the first item dropped)
-    if timings and flex and not args.no_calibrate and world > 1 and \
+    if full and timings and flex and not args.no_calibrate and world > 1 and \
             budget.allow("cost_model_fit", DROP_AT["cost_model_fit"]):
         calib = calibrate_model(comm, timings, nbytes, esize, world, x, y, op, dist, max_over_ranks, rank, shared,
                                 verify, world > 1 and not args.no_rccl and dtype != torch.float8_e4m3fn)
@@ -766,7 +800,8 @@ def main():
         hbm_tbps = round(hbm_bytes / t_step / 1e12, 3) if hbm_bytes else None
     except Exception:  # noqa: BLE001 - a schedule the model does not price: the fields stay empty
         hbm_tbps = link_rate = None
-    value = busbw  # rccl-tests busbw; 0 at N = 1 by definition (see the module docstring)
+    # rccl-tests busbw; at N = 1 busbw is 0 by definition, so the algbw of the timed steps (see the module docstring)
+    value = busbw if world > 1 else algbw
     readiness = None
     if world > 1 and isinstance(comm, Communicator):
         readiness = readiness_record(comm, creations)
@@ -795,7 +830,8 @@ def main():
             "parallelism": f"dp{world}",
             "algorithm": desc,
         },
-        "value_definition": "busbw (rccl-tests: algbw * 2(N-1)/N); 0 at N=1 by definition",
+        "value_definition": "busbw (rccl-tests: algbw * 2(N-1)/N)" if world > 1
+                            else "algbw (bytes / step time) of the device copy; busbw is 0 at N=1 by definition",
         "busbw_GBps": round(busbw, 2),
         "algbw_GBps": round(algbw, 2),
         "aggregate_busbw_GBps": round(busbw * world, 2),
@@ -817,11 +853,11 @@ def main():
                                  world > 1 and dtype != torch.float8_e4m3fn and not args.no_rccl and not host_ref,
                                  timed_fn, args.sweep_out)
     if world == 1:
-        out["note"] = ("N=1: no inter-GPU traffic, busbw = 0 by definition (value); algbw_GBps is the device copy "
-                       "through the flexar executor kernel and is not comparable with busbw")
-        if not args.no_reduce_kernel:  # outside the timed region; the headline `value` is unchanged
+        out["note"] = ("N=1: no inter-GPU traffic, busbw = 0 by definition; value = algbw_GBps is the device copy "
+                       "through the flexar executor kernel and is not comparable with the busbw of N >= 2")
+        if full and not args.no_reduce_kernel:  # outside the timed region; the headline `value` is unchanged
             out["reduce_kernel"] = run_reduce_kernel(dev, args.reduce_kernel_mb)
-        if not args.no_group_executor:
+        if full and not args.no_group_executor:
             out["group_executor"] = run_group_executor(dev)
     out["dropped"] = budget.dropped or None
     out["budget_s"] = budget.seconds

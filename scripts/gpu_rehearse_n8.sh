@@ -11,7 +11,7 @@ export FLEXAR_NO_BUILD=1 FLEXAR_BENCH_SHARED_GPU=1 FLEXAR_BENCH_SHARED_RCCL=1
 # then time-slices the processes and every cross-rank hand-off waits for a queue switch (~12 ms per call)
 export GPU_MAX_HW_QUEUES="${REHEARSE_HW_QUEUES:-2}"
 timeout -k 10 700 python3 -m torch.distributed.run --nnodes=1 --nproc-per-node 8 \
-    --master-addr 127.0.0.1 --master-port 29518 bench.py --gpus 8 --steps 10 --warmup 3 \
+    --master-addr 127.0.0.1 --master-port 29518 bench.py --gpus 8 --steps 10 --warmup 3 --full \
     > gpurun_out/rehearse_rccl_n8.log 2>&1 && echo "rehearse rccl n=8 ok"
 rc=$?
 grep '^{' gpurun_out/rehearse_rccl_n8.log > gpurun_out/bench_shared_rccl_n8.json 2>/dev/null

@@ -7,10 +7,10 @@ R="${GRAFT_REPO_ROOT:-$(pwd)}"
 cd "$R"; mkdir -p gpurun_out
 export FLEXAR_NO_BUILD=1 FLEXAR_BENCH_SHARED_GPU=1 FLEXAR_BENCH_SHARED_RCCL=1
 timeout -k 10 400 python3 -m torch.distributed.run --nnodes=1 --nproc-per-node 2 \
-    --master-addr 127.0.0.1 --master-port 29512 bench.py --gpus 2 --steps 10 --warmup 3 \
+    --master-addr 127.0.0.1 --master-port 29512 bench.py --gpus 2 --steps 10 --warmup 3 --full \
     > gpurun_out/rehearse_rccl_n2.log 2>&1 && echo "rehearse rccl n=2 ok" &&
 timeout -k 10 500 python3 -m torch.distributed.run --nnodes=1 --nproc-per-node 4 \
-    --master-addr 127.0.0.1 --master-port 29513 bench.py --gpus 4 --steps 10 --warmup 3 \
+    --master-addr 127.0.0.1 --master-port 29513 bench.py --gpus 4 --steps 10 --warmup 3 --full \
     > gpurun_out/rehearse_rccl_n4.log 2>&1 && echo "rehearse rccl n=4 ok"
 rc=$?
 tail -2 gpurun_out/rehearse_rccl_n2.log | cut -c1-1500; tail -2 gpurun_out/rehearse_rccl_n4.log 2>/dev/null | cut -c1-1500

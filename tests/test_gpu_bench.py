@@ -78,7 +78,7 @@ def _bench(extra_env, args, timeout=300):
     env = dict(os.environ, FLEXAR_BENCH_SHARED_GPU="1", FLEXAR_BENCH_SHARED_RCCL="1", FLEXAR_NO_BUILD="1", **extra_env)
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2",
            "--master-addr", "127.0.0.1", "--master-port", str(_port()), os.path.join(REPO, "bench.py"),
-           "--gpus", "2", "--steps", "3", "--warmup", "1", *args]
+           "--gpus", "2", "--steps", "3", "--warmup", "1", "--full", *args]
     r = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=timeout, cwd=REPO)
     _keep(r, "sections_" + "_".join(sorted(extra_env)) if extra_env else "sections")
     assert r.returncode == 0, _diag(r, "sections")
@@ -135,19 +135,63 @@ def test_bench_json_names_a_recovered_selftest_family(cuda):
     assert out["value"] > 0
 
 
+def test_bench_plain_n1_run_is_lean_and_dumps_its_outputs(cuda, tmp_path):
+    """A plain N = 1 run measures the headline alone (no companion section in its line) and `--dump-outputs`
+    writes what the last timed step returned as float32: a fixed sample of a result above the cap, the same
+    elements with the same values from run to run (seeded inputs), whatever the number of steps."""
+    import importlib.util
+
+    import numpy as np
+
+    spec = importlib.util.spec_from_file_location("bench_mod", os.path.join(REPO, "bench.py"))
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+    env = dict(os.environ, FLEXAR_NO_BUILD="1")
+    dumps = []
+    for name, steps in (("a", "2"), ("b", "4")):
+        r = subprocess.run([sys.executable, os.path.join(REPO, "bench.py"), "--gpus", "1", "--steps", steps, "--warmup", "1",
+                            "--size-mb", "32", "--dump-outputs", str(tmp_path / name)],
+                           env=env, capture_output=True, text=True, timeout=120, cwd=REPO)
+        assert r.returncode == 0, _diag(r, "n1_plain_" + name)
+        lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
+        assert len(lines) == 1, r.stdout[-2000:]
+        out = json.loads(lines[0])
+        assert out["steps"] == int(steps) and out["ms_per_step"] > 0, out
+        assert out["busbw_GBps"] == 0.0 and out["value"] == out["algbw_GBps"] > 0, out  # one rank: algbw
+        # the headline is the timed steps' own rate: bytes over ms_per_step (both rounded in the line)
+        assert out["value"] == pytest.approx((32 << 20) / (out["ms_per_step"] * 1e-3) / 1e9, rel=1e-2), out
+        assert "reduce_kernel" not in out and "group_executor" not in out, sorted(out)
+        assert sorted(p.name for p in (tmp_path / name).iterdir()) == ["allreduce_out.npy"]
+        dumps.append(np.load(tmp_path / name / "allreduce_out.npy"))
+    a, b = dumps
+    assert a.dtype == np.float32 and a.shape == (bench.DUMP_MAX_ELEMS,) and a.shape[0] < (32 << 20) // 4
+    assert np.array_equal(a, b)
+    # which elements, and of which tensor: with one rank the allreduce returns its input, rank 0's seeded randn
+    # (bench.py: generator seed 1234 + rank), and the sample is the sorted RandomState(20240607) draw of indices
+    import torch
+
+    count = (32 << 20) // 4
+    gen = torch.Generator(device=cuda)
+    gen.manual_seed(1234)
+    x = torch.randn(count, device=cuda, dtype=torch.float32, generator=gen).cpu().numpy()
+    pick = np.sort(np.random.RandomState(20240607).randint(0, count, size=bench.DUMP_MAX_ELEMS, dtype=np.int64))
+    assert pick[-1] >= bench.DUMP_MAX_ELEMS and not np.array_equal(x[pick], x[:bench.DUMP_MAX_ELEMS])  # no prefix
+    assert np.array_equal(a, x[pick])
+
+
 def test_bench_n1_line_carries_the_group_executor_section(cuda):
     """The driver's N = 1 line (no launcher): besides the headline it carries the 8-ranks-in-one-launch executor
     section, every schedule family of the 8-GPU node (the link-balanced channelled trees among them) exact on
     integer data, with a time and an effective HBM rate."""
     env = dict(os.environ, FLEXAR_NO_BUILD="1")
     r = subprocess.run([sys.executable, os.path.join(REPO, "bench.py"), "--steps", "3", "--warmup", "1",
-                        "--no-reduce-kernel"], env=env, capture_output=True, text=True, timeout=240, cwd=REPO)
+                        "--full", "--no-reduce-kernel"], env=env, capture_output=True, text=True, timeout=240, cwd=REPO)
     _keep(r, "n1_group_executor")
     assert r.returncode == 0, _diag(r, "n1_group_executor")
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
     assert len(lines) == 1, r.stdout[-2000:]
     out = json.loads(lines[0])
-    assert out["n_gpus"] == 1 and out["value"] == 0.0
+    assert out["n_gpus"] == 1 and out["busbw_GBps"] == 0.0 and out["value"] == out["algbw_GBps"] > 0
     rows = {row["spec"]: row for row in out["group_executor"]["rows"]}
     assert {"rhd+pull", "rhd:7+pull", "tree:4,2:7+pull", "flat+pull"} <= set(rows), rows
     for spec, row in rows.items():
